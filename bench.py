@@ -19,12 +19,18 @@ the only exchanges (RCCL).  Rank 0 prints ONE JSON line; at N=1 it also carries
   * ``extra.c2_aug_pil``: 5 steps (after 3) of c2 with the reference's in-step augmentation on the device inside the timed step,
   * ``extra.c2_cross_trainer`` / ``extra.c2_ori_trainer``: 3 steps (after 3) of the two other entry scripts' train bodies at the c2 shapes,
   * ``cpu_baseline``: the CPU oracle timed on the host cores.
+
+``--dump-outputs DIR`` writes what the last timed step of the headline leg computed (rank 0) as DIR/<name>.npy, float32 / float64:
+the dict the step returns (losses, pseudo labels) and the state it updated in place (prototypes, student and teacher weights); an output
+of more than DUMP_MAX_ELEMS elements is written as a fixed, seeded sample of its elements.  Every input of a leg is seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import contextlib
 import ctypes
 import json
 import os
+import random
 import socket
 import subprocess
 import sys
@@ -33,6 +39,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -177,6 +184,8 @@ def build(workload, dev, rank, dtype="bf16", mix="cutmix", aug="identity", force
     K, S, B, backbone, sup, Q, N, cfg_idx = WORKLOADS[workload]
     S, B = size or S, batch or B
     torch.manual_seed(3407)
+    np.random.seed(3407 + rank)           # the host draws of the step (cutmix boxes; the in-step augmentation also uses random)
+    random.seed(3407 + rank)
     cfg = {"Dataset": {"crop_size": (S, S), "scale_size": (0.5, 1.5) if aug == "pil" else (1.0, 1.0), "mix_mode": mix, "device_aug": aug}}
     bb = resnet.resnet101_tv(zero_init_residual=False) if backbone == "tv" else resnet.resnet101(zero_init_residual=False)
     with contextlib.redirect_stdout(sys.stderr):     # the constructor prints like the reference's; stdout carries the ONE JSON line only
@@ -214,10 +223,38 @@ def read_prof():
     return prof
 
 
-def timed_run(tr, batch, steps, warmup, world, dev, profile=True):
+DUMP_MAX_ELEMS = 1 << 22          # --dump-outputs: larger outputs are sampled (16 MB each in float32; at most three are: < 64 MB in all)
+
+
+def dump_outputs(tr, out, d):
+    """--dump-outputs: write the step's returned dict and the state it updated in place (prototypes, flat student / teacher weights) as
+    d/<name>.npy.  Floating outputs as float32 (float64 stays float64), integer ones (pseudo labels) as float32, exact below 2^24; an output
+    of more than DUMP_MAX_ELEMS elements as the flat sample at positions drawn once from a fixed seed (the same for every build)."""
+    arrays = dict(out, prototypes=tr.prototypes, student_params=tr.flat_p, teacher_params=tr.flat_ema)
+    host, positions = {}, {}
+    for name, t in arrays.items():
+        t = t.detach()
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            if n not in positions:
+                positions[n] = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values.to(t.device)
+            t = t.reshape(-1)[positions[n]]
+        if not t.is_floating_point():
+            assert t.numel() == 0 or int(t.abs().max()) < 2 ** 24, name
+        host[name] = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    assert total <= 64 << 20, total
+    os.makedirs(d, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    print(f"bench.py: {len(host)} outputs of the last timed step ({total / 2 ** 20:.1f} MB) -> {d}", file=sys.stderr)
+
+
+def timed_run(tr, batch, steps, warmup, world, dev, profile=True, dump_dir=None):
     """W untimed steps, then EXACTLY K timed steps bracketed by barrier + synchronize on both sides; MAX over ranks.
     Per-kernel HIP-event bracketing (roofline leg; ~2.8 us per event pair on the launch stream, ~2.6 ms per step) runs in ONE EXTRA
-    step after the timed region (r02 verdict, weak 14: the timed steps are all in one mode)."""
+    step after the timed region (r02 verdict, weak 14: the timed steps are all in one mode).  ``dump_dir``: the outputs of the last
+    timed step are written there (dump_outputs) between the timed region and that extra step, which would overwrite them."""
     from css_amd import _lib
 
     def sync():
@@ -234,6 +271,8 @@ def timed_run(tr, batch, steps, warmup, world, dev, profile=True):
         out = tr.step(*batch)
     sync()
     dt = time.perf_counter() - t0
+    if dump_dir:
+        dump_outputs(tr, out, dump_dir)
     if profile and not os.environ.get("CSS_BENCH_NOPROF"):
         _lib.lib().css_prof_enable(1)
         tr.step(*batch)
@@ -383,7 +422,11 @@ def main():
     ap.add_argument("--cpu-budget", type=float, default=150.0)
     ap.add_argument("--timeout", type=float, default=0.0, help="self-launcher (--gpus N without WORLD_SIZE): stop the ranks after this many "
                                                                "seconds (default: 600 + 30 per step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline leg computed as DIR/<name>.npy (rank 0; < 64 MB in all)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # ---- launch decision: BEFORE anything touches the GPU ----
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -431,9 +474,9 @@ def main():
             print(f"bench.py rank {rank}: rendezvous failed: {e}", file=sys.stderr)
             sys.exit(RC_RENDEZVOUS)
 
-    def run_leg(workload, steps, warmup, forced_valid, profile=True, size=None, batch=None, aug=None, script="mix"):
+    def run_leg(workload, steps, warmup, forced_valid, profile=True, size=None, batch=None, aug=None, script="mix", dump_dir=None):
         tr, batch_t, meta = build(workload, dev, rank, a.dtype, a.mix, aug or a.aug, forced_valid, size, batch, script)
-        dt, out, prof = timed_run(tr, batch_t, steps, warmup, world, dev, profile)
+        dt, out, prof = timed_run(tr, batch_t, steps, warmup, world, dev, profile, dump_dir)
         roof, kernels = rooflines(prof, a.dtype, workload, (7 if script == "ori" else 8) * meta["B"] * meta["fwd_flop"])
         losses = {k: round(float(v), 4) for k, v in out.items() if k != "pseudo"}
         del tr, batch_t
@@ -452,7 +495,8 @@ def main():
             except Exception:
                 pass
     fv = a.forced_valid or a.workload == "c5"
-    dt, losses, roof, kernels, meta = run_leg(a.workload, a.steps, a.warmup, fv, True, a.size, a.batch)
+    dt, losses, roof, kernels, meta = run_leg(a.workload, a.steps, a.warmup, fv, True, a.size, a.batch,
+                                              dump_dir=a.dump_outputs if rank == 0 else None)
     S, B, K = meta["S"], meta["B"], meta["K"]
     if rank == 0:
         shape = "VOC-shaped" if meta["backbone"] == "tv" else "Cityscapes-shaped"

@@ -4,7 +4,7 @@
 #   bash scripts/ab_env.sh VAR "v1 v2 ..." ["c2 c4"] [steps] [reps] [out]      e.g.   bash scripts/ab_env.sh CSS_SMALL_NST2 "0 1" "c2 c4" 10 2
 # Prints, per (value, workload, repetition): ms per step, images/s and the per-class kernel times of the profiled step.
 VAR=$1; VALS=${2:-"0 1"}; WLS=${3:-"c2"}; STEPS=${4:-10}; REPS=${5:-2}
-cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
+cd "$(dirname "$0")/.." || exit 1
 mkdir -p gpurun_out
 O=${6:-gpurun_out/ab_${VAR}.txt}; : > $O
 line() { python - "$1" <<'PY'

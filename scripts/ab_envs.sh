@@ -3,7 +3,7 @@
 #   bash scripts/ab_envs.sh OUT REPS STEPS WORKLOAD "CSS_A=1" "CSS_A=1 CSS_B=3" ""
 # Prints per (setting, repetition): ms per step, images/s and the per-class kernel times of the profiled step (as scripts/ab_env.sh).
 O=$1; REPS=$2; STEPS=$3; WL=$4; shift 4
-cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
+cd "$(dirname "$0")/.." || exit 1
 mkdir -p gpurun_out; : > $O
 for rep in $(seq 1 $REPS); do
   for s in "$@"; do

@@ -3,7 +3,7 @@
 # `timeout`; FETCH_SIZE and WRITE_SIZE never share a pass; no trace domains next to --pmc).  Usage: scripts/collect_profiles.sh r02
 set -u
 TAG=${1:-r02}
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 # what these profiles were measured on (checked by tests/test_host_cpu.py against the working tree)

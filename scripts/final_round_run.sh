@@ -3,7 +3,7 @@
 # (the default bench line replays the traffic files they produce), then the bench lines, the forced-collectives lines (RCCL and the peer
 # exchange in loop-back), smoke(), and the whole GPU suite.  Usage: bash scripts/final_round_run.sh r05   (TAG = the round: every output is gpurun_out/<TAG>_*)
 TAG=${1:-r05}
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$0")/.." || exit 1
 ROOT=$(pwd)
 mkdir -p gpurun_out
 rm -f gpurun_out/${TAG}_profile_errors.txt

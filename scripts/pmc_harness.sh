@@ -2,7 +2,7 @@
 # PMC passes over the conv harness (one shape per run): usage  scripts/pmc_harness.sh <shape index> <tag>   (on the GPU box)
 # each counter group is its own rocprofv3 run (block slot limits; FETCH_SIZE / WRITE_SIZE never share a pass)
 set -u
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 IDX=$1; TAG=$2
 export CB_ONLY=$IDX CB_NOWGRAD=1 CB_STATS=1
 cd /tmp && export TMPDIR=/tmp

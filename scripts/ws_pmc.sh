@@ -2,7 +2,7 @@
 # PMC passes over the conv_ws harness (on the GPU box): usage scripts/ws_pmc.sh <shape index> <tag>
 # each counter group is its own rocprofv3 run (FETCH_SIZE / WRITE_SIZE never share a pass); FETCH_SIZE / WRITE_SIZE are in KB
 set -u
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 IDX=$1; TAG=$2
 export WB_ONLY=$IDX WB_REPS=5
 cd /tmp && export TMPDIR=/tmp

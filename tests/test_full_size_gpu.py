@@ -218,3 +218,31 @@ def test_undamped_step_vs_oracle_65_fp32():
     fl_m = max((ri["pseudo"] != ro["pseudo"]).float().mean().item() for ri, _ in floors)
     print(f"undamped 65^2 step fp32: prototypes rel {e:.2e} (floor {fl:.2e}), pseudo labels mismatching {mism:.2e} (floor {fl_m:.2e})")
     assert e < max(1e-3, 2 * fl) and mism < max(5e-3, 2 * fl_m), (e, fl, mism, fl_m)
+
+
+def test_bench_dump_outputs_are_the_last_timed_step_and_reproducible(tmp_path):
+    """bench.py --dump-outputs: two fresh runs with the same arguments write the same outputs bit for bit (every input is seeded); the
+    second runs without the per-kernel profiling step that follows the timed region, so equality also shows the dump precedes it."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for tag, extra_env in (("a", {}), ("b", {"CSS_BENCH_NOPROF": "1"})):
+        d = tmp_path / tag
+        env = dict(os.environ, **extra_env)
+        env.pop("WORLD_SIZE", None)
+        env.pop("RANK", None)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--size", "65", "--batch", "2",
+                            "--no-extra", "--no-cpu-baseline", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["steps"] == 3
+        runs.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    a, b = runs
+    assert sorted(a) == ["contrast", "prototypes", "pseudo", "student_params", "sup", "teacher_params", "total", "unsup"]
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), k
+        assert np.array_equal(a[k], b[k], equal_nan=True), k
+    assert all(np.isfinite(a[k]).all() for k in ("prototypes", "student_params", "teacher_params"))

@@ -369,6 +369,33 @@ def test_bench_refuses_a_world_size_mismatch():
     assert r.returncode != 0 and "WORLD_SIZE=4" in r.stderr
 
 
+def test_bench_refuses_zero_timed_steps():
+    r = _run_bench(["--steps", "0"], {})
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_samples_large_ones(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on a stand-in trainer: every returned tensor and the updated state as DIR/<name>.npy in float32 (float64
+    kept), integer labels exact, an output above DUMP_MAX_ELEMS as the same seeded sample on every call (student and teacher alike)."""
+    import types
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    flat = torch.arange(5000, dtype=torch.float32)
+    tr = types.SimpleNamespace(prototypes=torch.randn(3, 8), flat_p=flat, flat_ema=flat * 2)
+    out = dict(sup=torch.tensor(1.5, dtype=torch.bfloat16), total=torch.tensor(2.0, dtype=torch.float64), pseudo=torch.tensor([[-1, 20], [3, 4]]))
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(tr, out, str(d))
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(a) == ["prototypes", "pseudo", "student_params", "sup", "teacher_params", "total"]
+    assert a["sup"].dtype == np.float32 and a["sup"] == 1.5 and a["total"].dtype == np.float64 and a["total"] == 2.0
+    assert a["pseudo"].dtype == np.float32 and a["pseudo"].tolist() == [[-1, 20], [3, 4]]
+    assert np.array_equal(a["prototypes"], tr.prototypes.numpy())
+    s, t = a["student_params"], a["teacher_params"]
+    assert s.shape == (1000,) and len(np.unique(s)) == 1000 and np.array_equal(t, 2 * s)
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+
+
 def test_conv_ws_kernel_isa_and_shape_rules(tmp_path):
     """conv_ws_kernel (csrc/conv_ws.hip) waits for its LDS-DMA pieces by COUNT (loads, stores and LDS-DMA retire in order): the K loop must
     hold exactly the waits the source states and no compiler-inserted drain, no scratch, the whole 160 KiB ring in ONE LDS object; and the
